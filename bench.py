@@ -14,7 +14,13 @@ fsdp_workers.py:174-196). ``--balance`` reorders the batch with the Karmarkar-Ka
 (ray_trainer.py:1064-1079), which splits groups over ranks and exercises the cross-rank GRPO
 statistics. ``--scaling weak`` gives every rank its own full 512 x 1024 batch.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+  A plain run sets up, warms up, times the K steps and prints the result line (``ms_per_step``: the
+  milliseconds one timed step took). ``--dump-outputs DIR`` also writes what the last timed step
+  handed back as DIR/<name>.npy. ``--full`` adds everything else the benchmark measures or checks:
+  per-kernel HIP-event timing and the rooflines, the CPU baseline, the exposed / isolated
+  all-reduce times, the reduced final metrics, the clipped-branch token counts and the replica
+  check (the replica check also runs without it whenever there is more than one rank).
   N > 1 without a launcher: bench.py starts ``torch.distributed.run`` as a CHILD process (before
   any GPU call; no exec) with N ranks on 127.0.0.1 and exits with its return code.
 Rank 0 prints ONE JSON line (see the driver contract in the task statement).
@@ -196,8 +202,15 @@ def parse(argv=None):
                          "dlogits backward, no [N, V] logits in HBM)")
     ap.add_argument("--no-rmpad", action="store_true")
     ap.add_argument("--no-mixed-precision", action="store_true", help="fp32 weights + autocast instead of bf16/fp32-master")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: per-kernel timing + rooflines, the CPU "
+                         "baseline, all-reduce timing, final metrics, clipped-branch token counts, the replica check")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps rank 0 writes what the last timed step returned (old log-probs, "
+                         "entropies, advantages, returns, the update's metrics, a strided sample of the updated fp32 "
+                         "masters) as DIR/<name>.npy, at most 64 MB in all")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="with --full: skip the per-kernel event timing")
     ap.add_argument("--cpu-sample-rows", type=int, default=2048,
                     help="response tokens per repetition of the CPU baseline's log-prob fwd+bwd sample")
     ap.add_argument("--cpu-reps", type=int, default=5, help="timed repetitions (after 1 warm-up) of the CPU baseline")
@@ -212,7 +225,10 @@ def parse(argv=None):
                          "small CPU module and print a JSON line (no GPU work)")
     ap.add_argument("--responses", choices=["dense", "realistic"], default="dense",
                     help="response lengths: dense (all R valid) or realistic (U[128, R], SURVEY §8d)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 _T0 = time.perf_counter()
@@ -403,6 +419,51 @@ def dump_state(path: str, init, worker, metrics, rank: int):
                     if isinstance(v, (list, float, int))})
 
 
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000  # --dump-outputs: all files together stay below this
+
+
+def _fixed_sample(a, max_bytes: int):
+    """`a` itself when it fits in max_bytes, else a fixed (seed 0) sample of its elements in index order."""
+    import numpy as np
+
+    flat = a.reshape(-1)
+    keep = max_bytes // flat.itemsize
+    if flat.size <= keep:
+        return a
+    idx = np.sort(np.random.default_rng(0).choice(flat.size, size=keep, replace=False, shuffle=False))
+    return flat[idx]
+
+
+def dump_outputs(path: str, last: dict, batch, worker, rank: int):
+    """--dump-outputs: the arrays the last timed step handed to its caller, one DIR/<name>.npy each.
+
+    compute_log_prob's ``old_log_probs`` and ``entropys``, compute_advantage's ``advantages`` and
+    ``returns`` (this rank's rows, [B, R] float32), update_actor's metrics (``metrics.<key>``,
+    float64, one entry per micro-batch; the perf/* entries are measurements of the run, not results,
+    and stay out) and the weights the update left (``masters_sample``: every 997th element of the
+    fp32 masters in bucket order). Arrays that would take the total past 64 MB are cut to a fixed
+    seeded sample. Every rank must call this (the ZeRO shards are gathered); rank 0 writes."""
+    import numpy as np
+
+    arrays = {"masters_sample": master_sample(worker).numpy()}
+    for name in ("old_log_probs", "entropys"):
+        if last.get(name) is not None:
+            arrays[name] = last[name].detach().float().cpu().numpy()
+    for name in ("advantages", "returns"):
+        if name in batch.batch.keys():
+            arrays[name] = batch.batch[name].detach().float().cpu().numpy()
+    if rank != 0:
+        return
+    small = {}
+    for k, v in (last.get("metrics") or {}).items():
+        if not k.startswith("perf/") and isinstance(v, (list, float, int)):
+            small["metrics." + k.replace("/", "__")] = np.atleast_1d(np.asarray(v, dtype=np.float64))
+    share = (DUMP_BUDGET_BYTES - sum(v.nbytes for v in small.values())) // len(arrays)
+    os.makedirs(path, exist_ok=True)
+    for name, a in {**small, **{k: _fixed_sample(v, share) for k, v in arrays.items()}}.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def shard_batch(args, rank: int, world: int, dev):
     """This rank's DataProto shard of the benchmark batch.
 
@@ -554,9 +615,12 @@ def main():
         batch.batch["ref_log_prob"] = lp0 + 0.1 * ref_noise
     del lp0, ref_noise
 
+    last = {}  # what the latest step's calls returned (--dump-outputs)
+
     def step():
         out = worker.compute_log_prob(batch)
         old = out.batch["old_log_probs"]
+        last["old_log_probs"], last["entropys"] = old, out.batch["entropys"]
         if args.old_noise:
             # old = new + N(0, 0.05^2) so the timed step exercises the clip branches
             old = old + args.old_noise * old_noise
@@ -570,9 +634,9 @@ def main():
         torch.cuda.synchronize()
         log(rank, f"warmup step {i} done")
     torch.cuda.synchronize()
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         K.TIMER = K.KernelTimer()
-    comm_timer = worker.actor.grad_reducer.start_timing() if world > 1 else None
+    comm_timer = worker.actor.grad_reducer.start_timing() if args.full and world > 1 else None
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -616,7 +680,7 @@ def main():
     ksum = K.TIMER.summary() if K.TIMER is not None else {}
     K.TIMER = None
     comm = None
-    if world > 1:
+    if args.full and world > 1:
         exposed_ms = worker.actor.grad_reducer.stop_timing()
         ex = torch.tensor([exposed_ms / args.steps], dtype=torch.float64, device=dev)
         vcomm.all_reduce(ex, op=dist.ReduceOp.MAX)
@@ -633,29 +697,37 @@ def main():
     perf_throughput = sum(batch.meta_info["global_token_num"]) * args.steps / elapsed / world
 
     log(rank, f"timed region: {elapsed:.2f}s for {args.steps} steps")
-    # the reference's reduction of the last step's metric lists (utils/metric/utils.py:23-50: mean,
-    # max / min by key name), then over the ranks as its DP collect does; and the clipped-branch
-    # token counts of all timed steps, summed over the ranks
-    from verl_amd.trainer.ppo.trainer_step import reduce_metrics_dp
+    if args.dump_outputs:
+        last["metrics"] = metrics.meta_info["metrics"]
+        dump_outputs(args.dump_outputs, last, batch, worker, rank)
+        log(rank, f"outputs of the last timed step written to {args.dump_outputs}")
+    final_metrics, clip = None, None
+    if args.full:
+        # the reference's reduction of the last step's metric lists (utils/metric/utils.py:23-50: mean,
+        # max / min by key name), then over the ranks as its DP collect does; and the clipped-branch
+        # token counts of all timed steps, summed over the ranks
+        from verl_amd.trainer.ppo.trainer_step import reduce_metrics_dp
 
-    final_metrics = reduce_metrics_dp(dict(metrics.meta_info["metrics"])) if metrics is not None else {}
-    clip = clipped_tokens(step_metrics, batch, micro, args.dynamic_bsz > 0)
-    if clip is not None and world > 1:
-        ct = torch.tensor([clip[k] for k in sorted(clip)], dtype=torch.float64, device=dev)
-        vcomm.all_reduce(ct)
-        clip = {k: round(float(v)) for k, v in zip(sorted(clip), ct.tolist())}
+        final_metrics = reduce_metrics_dp(dict(metrics.meta_info["metrics"]))
+        clip = clipped_tokens(step_metrics, batch, micro, args.dynamic_bsz > 0)
+        if clip is not None and world > 1:
+            ct = torch.tensor([clip[k] for k in sorted(clip)], dtype=torch.float64, device=dev)
+            vcomm.all_reduce(ct)
+            clip = {k: round(float(v)) for k, v in zip(sorted(clip), ct.tolist())}
     # after the timed region: every rank must hold the same model (FSDP's by-construction
-    # consistency, fsdp_workers.py:370-405) and the same globally-reduced metrics
-    from verl_amd.utils.replica_check import replica_check
+    # consistency, fsdp_workers.py:370-405) and the same globally-reduced metrics; one rank is
+    # trivially identical, so N = 1 checks (and checksums its weights) only with --full
+    rcheck = None
+    if args.full or world > 1:
+        from verl_amd.utils.replica_check import replica_check
 
-    rcheck = replica_check(worker.module, worker.actor.grad_reducer,
-                           metrics.meta_info["metrics"] if metrics is not None else {},
-                           ["actor/grad_norm", "actor/lr"], elapsed - fastest)
-    log(rank, f"replica check: {rcheck}")
+        rcheck = replica_check(worker.module, worker.actor.grad_reducer, metrics.meta_info["metrics"],
+                               ["actor/grad_norm", "actor/lr"], elapsed - fastest)
+        log(rank, f"replica check: {rcheck}")
     if args.dump_state:
         dump_state(args.dump_state, init_sample, worker, metrics, rank)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:  # the contract: rank 0 at N = 1 only
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:  # the contract: rank 0 at N = 1 only
         cpu = cpu_baseline(args)
         log(rank, f"cpu baseline: {cpu['value']} tokens/s on {cpu['cores']} threads")
 
@@ -706,6 +778,7 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": round(1e3 * elapsed / args.steps, 2),
+            "full": args.full,
             "higher_is_better": True,
             "scaling": args.scaling,
             "vs_baseline": None,
@@ -775,7 +848,7 @@ def main():
             "kernels": {k: {kk: (round(vv, 3) if isinstance(vv, float) else vv) for kk, vv in v.items()}
                         for k, v in ksum.items()},
             "cpu_baseline": cpu,
-            "replicas_identical": rcheck["replicas_identical"],
+            "replicas_identical": rcheck["replicas_identical"] if rcheck else None,
             "replica_check": rcheck,
             "final_metrics": final_metrics,
             "final_metrics_reduction": "reduce_metrics (utils/metric/utils.py:23-50) of the last timed step, "
@@ -789,7 +862,7 @@ def main():
                 f.write(s + "\n")
     if world > 1:
         dist.destroy_process_group()
-    if not rcheck["replicas_identical"]:
+    if rcheck is not None and not rcheck["replicas_identical"]:
         print(f"[bench] rank {rank}: replicas differ after the run: {rcheck}", file=sys.stderr, flush=True)
         sys.exit(4)
 

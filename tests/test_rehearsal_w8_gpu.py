@@ -26,7 +26,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SMALL = ["--prompts", "8", "--response-len", "256", "--prompt-len", "128", "--steps", "1", "--warmup", "1",
-         "--no-cpu-baseline", "--no-kernel-timing"]
+         "--full", "--no-cpu-baseline", "--no-kernel-timing"]
 
 
 def _bench(tmp, name, gpus, extra=(), scratch=None):
@@ -57,7 +57,18 @@ def test_bench_world8_gloo_rehearsal_matches_world1(tmp_path):
     torch.cuda.empty_cache()
     tmp = os.environ.get("VA_REHEARSAL_OUT") or str(tmp_path)  # keep the JSON lines and logs when asked
     os.makedirs(tmp, exist_ok=True)
-    r1, d1 = _bench(tmp, "w1", 1, scratch=str(tmp_path))
+    outs = tmp_path / "outputs_w1"
+    r1, d1 = _bench(tmp, "w1", 1, ("--dump-outputs", str(outs)), scratch=str(tmp_path))
+    # --dump-outputs: what the last timed step returned, as float32 / float64 .npy files under 64 MB
+    dumped = {p.stem: np.load(p) for p in outs.glob("*.npy")}
+    assert {"old_log_probs", "entropys", "advantages", "returns", "masters_sample",
+            "metrics.actor__grad_norm", "metrics.actor__pg_loss"} <= set(dumped), sorted(dumped)
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in dumped.values())
+    assert sum(a.nbytes for a in dumped.values()) <= 64e6
+    for name in ("old_log_probs", "entropys", "advantages", "returns"):
+        assert dumped[name].shape == (64, 256), (name, dumped[name].shape)
+    assert np.array_equal(dumped["masters_sample"], d1["masters"])  # the weights the last update left
+    assert float(dumped["metrics.actor__grad_norm"][-1]) == float(d1["actor__grad_norm"].reshape(-1)[-1])
     u1 = d1["masters"].astype(np.float64) - d1["masters_init"]
     g1 = float(d1["actor__grad_norm"].reshape(-1)[-1])
     assert np.linalg.norm(u1) > 0

@@ -9,7 +9,7 @@
 #   suite                 full GPU test suite              -> pytest_gpu.log
 #   tests:<pytest args>   a subset, e.g. "tests:tests/test_weight_grad_gpu.py -k tile" -> pytest_<n>.log
 #   smoke                 __graft_entry__.smoke()          -> smoke.log
-#   bench[:<tag>[:<args>]] bench.py as the driver runs it (+ args) -> bench_<tag>.json / .log
+#   bench[:<tag>[:<args>]] bench.py --full (+ args)          -> bench_<tag>.json / .log
 #   rocprof[:<tag>[:<args>]] the bench command (+ args) under rocprofv3 --kernel-trace --stats -> kernel_stats_<tag>*,
 #                         trace_gaps_<tag>.txt, bench_under_rocprof_<tag>.json
 #   pmc_f1                tools/f1_pmc.sh                  -> pmc_f1_product.json
@@ -53,16 +53,16 @@ for step in "$@"; do
     bench*)
       IFS=: read -r _ tag args <<< "$step"; tag=${tag:-default}
       # shellcheck disable=SC2086
-      run 500 "$O/bench_$tag.log" python bench.py --out "$O/bench_$tag.json" $args
-      echo "# cmd: python bench.py --out $O/bench_$tag.json $args" > "$O/bench_$tag.json.cmd"
+      run 500 "$O/bench_$tag.log" python bench.py --full --out "$O/bench_$tag.json" $args
+      echo "# cmd: python bench.py --full --out $O/bench_$tag.json $args" > "$O/bench_$tag.json.cmd"
       python -c "import json;d=json.load(open('$O/bench_$tag.json'));r=d['roofline'];print('bench $tag', d['value'], d['ms_per_step'], r['kernel'], r['frac'], d.get('config',{}).get('peak_hbm_gb'))" ;;
     rocprof*)
       IFS=: read -r _ tag args <<< "$step"; tag=${tag:-headline}
       # shellcheck disable=SC2086
-      run 600 "$O/bench_prof_$tag.log" rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_$tag" -o "$tag" -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --out "$O/bench_under_rocprof_$tag.json" $args
+      run 600 "$O/bench_prof_$tag.log" rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_$tag" -o "$tag" -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --out "$O/bench_under_rocprof_$tag.json" $args
       st=$(find "$O/prof_$tag" -name "*kernel_stats.csv" | head -1)
       kt=$(find "$O/prof_$tag" -name "*kernel_trace.csv" | head -1)
-      { echo "# cmd: rocprofv3 --kernel-trace --stats -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline; python tools/prof_summary.py"; python tools/prof_summary.py "$st"; } > "$O/kernel_stats_${tag}_summary.txt"
+      { echo "# cmd: rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline; python tools/prof_summary.py"; python tools/prof_summary.py "$st"; } > "$O/kernel_stats_${tag}_summary.txt"
       cp "$st" "$O/kernel_stats_$tag.csv"
       { echo "# cmd: python tools/trace_gaps.py <kernel_trace> --steps 3 --top 12"; python tools/trace_gaps.py "$kt" --steps 3 --top 12 | tail -16; } > "$O/trace_gaps_$tag.txt"
       gzip -c "$kt" > "$O/kernel_trace_$tag.csv.gz" && rm -rf "$O/prof_$tag"
